@@ -16,10 +16,18 @@ data-path collective (the layers are independent).  value = the 
 bytes / max-over-ranks time.  For the 7B model at N > 1 the weak-scaling figure (every rank
 quantizes a full 7B) is reported beside it ("weak").
 
-Also reported: "roofline" for the quantize kernel (algorithmic bytes / measured HIP-event time vs
-8 TB/s), "traffic" from a committed rocprofv3 PMC summary stamped with the kernel sources' hash
-(dropped when the sources changed since), and "cpu_baseline": the reference's CPU arithmetic
-(oracle/torch_ref.py, pinned to the reference) timed on a bounded sample on rank 0.
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: set up, ramp the
+clock, W warmup steps, the K timed steps, then the result line.  Its "roofline" is the quantize
+kernel's algorithmic bytes / measured HIP-event time of those K steps vs 8 TB/s, with "traffic" from a
+committed rocprofv3 PMC summary stamped with the kernel sources' hash (dropped when the sources
+changed since).  `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs).
+
+`--full` adds every other measurement, each in runs of its own after (the copy ceilings: before)
+the timed steps: the in-run copy ceilings of the roofline, the other placement, the cold single calls
+per Llama shape, "cpu_baseline" (the reference's CPU arithmetic, oracle/torch_ref.py, pinned to the
+reference, timed on a bounded sample on rank 0), the PPL-harness plumbing run, the configs[2] / [3] /
+[4] sections, and at N > 1 the gather / scatter collectives and the weak-scaling figure.  The
+`--no-*` options switch single parts of a `--full` run off.
 """
 import argparse
 import json
@@ -84,6 +92,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: copy ceilings, other placement, per-shape cold calls, CPU baseline, "
+                         "PPL plumbing, the configs[2]/[3]/[4] sections, and at N > 1 the collectives and the "
+                         "weak-scaling figure (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (dequantized weights, scales, "
+                         "zeros: a fixed seeded sample plus per-tensor sums) as DIR/<name>.npy")
     ap.add_argument("--bits", type=int, default=4)
     ap.add_argument("--group", type=int, default=128)
     ap.add_argument("--symmetric", action="store_true")
@@ -94,7 +109,7 @@ def parse():
                     help="headline = weak scaling instead: every rank quantizes the full model")
     ap.add_argument("--no-weak", action="store_true", help="7B at N > 1: skip the secondary weak-scaling figure")
     ap.add_argument("--gather", action="store_true",
-                    help="(default at N > 1, kept for old command lines) time the rooted gather of the packed "
+                    help="(default of --full at N > 1, kept for old command lines) time the rooted gather of the packed "
                          "codes + scales/zeros to rank 0 over RCCL, reported separately (never in value)")
     ap.add_argument("--no-collectives", action="store_true",
                     help="N > 1: skip the separately timed RCCL gather / scatter (gather_ms, scatter_ms)")
@@ -125,7 +140,13 @@ def parse():
     ap.add_argument("--mark-file", default="",
                     help="write the host-clock interval of every timed region (JSONL) for tools/trace_sections.py "
                          "(cuts a rocprofv3 kernel trace of this run into the bench's rows)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: the headline's timed steps and nothing beside them
+        args.no_cpu_baseline = args.no_ppl = args.no_shapes = args.no_sections = True
+        args.no_collectives = args.no_weak = True
+    return args
 
 
 def _free_port():
@@ -395,7 +416,7 @@ def time_gather(plan, names, all_shapes, args, ws_n):
 
 
 def gather_section(plan, names, all_shapes, args, ws_n):
-    """N > 1, default: the packed results of this rank's bin (codes + scales/zeros, what a rank would
+    """N > 1, --full: the packed results of this rank's bin (codes + scales/zeros, what a rank would
     hand back) produced by one codes-writing launch over the same weights (outside the headline's
     timed region), then the rooted gather to rank 0 timed alone (shard.gather_to_rank0: one
     point-to-point send per rank, every receive posted together on rank 0)."""
@@ -411,7 +432,7 @@ def gather_section(plan, names, all_shapes, args, ws_n):
 
 
 def scatter_section(model, rank, ws_n):
-    """N > 1, default (bounded): the whole model's fp16 weights from rank 0 to their owners
+    """N > 1, --full (bounded): the whole model's fp16 weights from rank 0 to their owners
     (shard.scatter_from_rank0 over RCCL, one send per destination, all in flight), timed alone after
     a small warm-up transfer; the received buffers are dropped again."""
     _, _, _, ms, nbytes = scatter_weights(model, rank, ws_n)
@@ -764,6 +785,50 @@ def _timed_steps(plan, args, ws_n, stream, region):
     return kernel_ms, max_over_ranks(wall, ws_n) / args.steps * 1e3
 
 
+DUMP_SAMPLE_BYTES = 60 << 20  # all ranks' float32 samples together (the whole dump stays under 64 MB)
+DUMP_SEED = 20240531
+
+
+def dump_outputs(plan, names, all_shapes, out_dir, rank, ws_n):
+    """--dump-outputs: what the last timed step left in the plan's output buffers (what a caller of the
+    batched launch receives), for comparing two builds output for output.  A 7B model's outputs are
+    13 GB, so per tensor the files hold a fixed sample of flat element positions (drawn with
+    replacement from a generator seeded by the weight's index in the model; a tensor smaller than
+    its share is written whole) and the exact sum over the whole tensor:
+
+        dequant_sample.npy, scales_sample.npy, zeros_sample.npy   float32, the tensors' samples concatenated
+        dequant_sum.npy,    scales_sum.npy,    zeros_sum.npy      float64, one entry per tensor
+
+    in this rank's tensor order (rank r > 0 writes <name>_rank<r>.npy; no zeros files when symmetric).
+    The sums are exact in float64 for fp16 values below 1 in magnitude (multiples of 2^-24, at most
+    2^26 of them), whatever order the device adds them in.  The inputs are the counter generator's
+    (oracle/synth.py), identical from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    index = {n: i for i, (n, _) in enumerate(all_shapes)}
+    floats = DUMP_SAMPLE_BYTES // 4 // ws_n // len(names)  # this rank's float32 budget per tensor
+    share = {"dequant": floats * 3 // 4, "scales": floats // 8, "zeros": floats // 8}
+    kinds = {"dequant": plan.outs, "scales": plan.scales}
+    if not plan.symmetric:
+        kinds["zeros"] = plan.zeros
+    torch.cuda.synchronize()
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for k, (kind, tensors) in enumerate(kinds.items()):
+        samples, sums = [], []
+        for name, t in zip(names, tensors):
+            flat = t.reshape(-1)
+            if flat.numel() > share[kind]:
+                rng = np.random.default_rng([DUMP_SEED, k, index[name]])
+                pos = torch.from_numpy(rng.integers(0, flat.numel(), size=max(1, share[kind]), dtype=np.int64))
+                flat_s = flat[pos.to(flat.device)]
+            else:
+                flat_s = flat
+            samples.append(flat_s.float().cpu().numpy())
+            sums.append(float(flat.sum(dtype=torch.float64).item()))
+        np.save(os.path.join(out_dir, f"{kind}_sample{suffix}.npy"), np.concatenate(samples).astype(np.float32))
+        np.save(os.path.join(out_dir, f"{kind}_sum{suffix}.npy"), np.asarray(sums, dtype=np.float64))
+
+
 def all_ranks_sum(x, ws_n):
     if ws_n == 1:
         return x
@@ -861,7 +926,7 @@ def roofline_record(per_rank, kernel_name, traffic, traffic_src, ceiling=None, o
 
 
 # ---------------------------------------------------------------------------------------------
-# Extra sections of the default run: BASELINE configs[2] (fused forward), configs[4] (FP formats),
+# Extra sections of a --full run: BASELINE configs[2] (fused forward), configs[4] (FP formats),
 # configs[3] (Llama-2-70B) -- bounded, after the headline's timed region
 # ---------------------------------------------------------------------------------------------
 MFMA_PEAK_TFLOPS = 2500.0  # dense fp16 MFMA (MI355X_MICROARCH.md chip table; never the sparse figure)
@@ -1180,12 +1245,16 @@ def main():
     if args.variants:
         ab_variants(plan, [int(v) for v in args.variants.split(",")], args)
     clock_ramp(plan, args.ramp_seconds)
-    ceiling = copy_ceiling(plan)  # every rank: its own GPU's ceiling (roofline.per_rank)
-    fresh = fresh_ceiling(plan)   # and the box's, on buffers that are not the plan's
+    ceiling = fresh = None
+    if args.full:
+        ceiling = copy_ceiling(plan)  # every rank: its own GPU's ceiling (roofline.per_rank)
+        fresh = fresh_ceiling(plan)   # and the same GPU's on buffers that are not the plan's
     kernel_ms, ms_per_step = timed_steps(plan, args, ws_n, stream)
+    if args.dump_outputs:
+        dump_outputs(plan, names, all_shapes, args.dump_outputs, rank, ws_n)
 
     other = None
-    if ws_n == 1 and not args.inplace:
+    if args.full and ws_n == 1 and not args.inplace:
         other = other_placement_kernel(weights, plan, args)
 
     shapes_rec = None
@@ -1199,7 +1268,7 @@ def main():
     total_numel = all_ranks_sum(numel, ws_n)
     groups = numel // args.group
     alg_bytes = numel * 2 + numel * 2 + groups * 2 * (1 if args.symmetric else 2)  # read w, write deq, s(,z)
-    per_rank = gather_per_rank([kernel_ms, alg_bytes, ceiling["GBps"]], ws_n)
+    per_rank = gather_per_rank([kernel_ms, alg_bytes, ceiling["GBps"] if ceiling else 0.0], ws_n)
     if ws_n == 1:
         if args.model == "llama2-70b":
             traffic, traffic_src = committed_traffic(args.traffic_70b_file, numel, args.bits, args.group, "in-place")

@@ -445,3 +445,26 @@ def test_bench_summary_is_last_and_compact():
     assert s["formats_frac"]["fp4_e2m1_g128_asym_pack"] == 0.67 and s["llama2_70b_frac"] == 0.74
     assert len(json.dumps(s)) < 2000
     assert set(b.summary_of({"roofline": {"frac": 0.7}})) >= {"frac"}  # sections absent (N > 1 runs)
+
+
+def test_bench_plain_run_times_the_headline_only(monkeypatch):
+    """bench.py's options: a plain `--gpus 1 --steps K --warmup W` run has every measurement beside
+    the headline switched off; --full leaves each of them on unless its own --no-* option is given."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location(
+        "bench_for_options", os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    extras = ("no_cpu_baseline", "no_ppl", "no_shapes", "no_sections", "no_collectives", "no_weak")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert not a.full and a.steps == 7 and a.warmup == 2 and a.dump_outputs == ""
+    assert all(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-ppl", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_ppl
+    assert not any(getattr(a, k) for k in extras if k != "no_ppl")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()

@@ -210,7 +210,7 @@ def test_bench_gpus2_spawns_ranks_and_rooted_gather_moves_each_byte_once():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--full",
                         "--model", "opt-125m"], capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -256,7 +256,7 @@ def test_bench_gpus8_dry_run_rehearses_the_eight_rank_path():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["OMP_NUM_THREADS"] = "1"
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--dry-run", "--full",
                         "--model", "opt-125m"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     wall = time.perf_counter() - t0
     assert r.returncode == 0, r.stderr[-3000:]

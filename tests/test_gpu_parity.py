@@ -284,6 +284,55 @@ def test_batched_matches_single(K):
                 assert torch.equal(plan.zeros[i].view(torch.int16), r.zeros.view(torch.int16))
 
 
+def test_bench_dump_outputs_holds_the_plans_outputs(K, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: per tensor a seeded sample (a tensor within its share: whole) and the
+    exact float64 sum of the dequantized weights, scales and zeros that the batched launch left in the
+    plan; float32 / float64 .npy, the same files from call to call, no zeros files when symmetric."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "bench_for_dump", os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    shapes = [("a", (256, 512)), ("b", (64, 2048)), ("c", (8, 128))]
+    ws = []
+    for i, (_, s) in enumerate(shapes):
+        t = torch.empty(s, dtype=torch.float16, device=DEV)
+        K.fill_synthetic(t, 40 + i)
+        ws.append(t)
+    names = [n for n, _ in shapes]
+    # 3 tensors share 4 * 3 * 8192 bytes: 8192 floats each -> 6144 dequant, 1024 scales, 1024 zeros
+    monkeypatch.setattr(b, "DUMP_SAMPLE_BYTES", 4 * 3 * 8192)
+    for sym in (False, True):
+        plan = K.BatchPlan(ws, 4, 128, sym)
+        plan.run()
+        torch.cuda.synchronize()
+        d1, d2 = tmp_path / f"one{sym}", tmp_path / f"two{sym}"
+        b.dump_outputs(plan, names, shapes, str(d1), 0, 1)
+        b.dump_outputs(plan, names, shapes, str(d2), 0, 1)
+        kinds = {"dequant": plan.outs, "scales": plan.scales}
+        if not sym:
+            kinds["zeros"] = plan.zeros
+        assert sorted(os.listdir(d1)) == sorted(f"{k}_{p}.npy" for k in kinds for p in ("sample", "sum"))
+        for kind, tensors in kinds.items():
+            share = 6144 if kind == "dequant" else 1024
+            full = [to_np(t).reshape(-1).astype(np.float32) for t in tensors]
+            sample, sums = np.load(d1 / f"{kind}_sample.npy"), np.load(d1 / f"{kind}_sum.npy")
+            assert sample.dtype == np.float32 and sums.dtype == np.float64
+            assert np.array_equal(sample, np.load(d2 / f"{kind}_sample.npy"))
+            assert np.array_equal(sums, np.load(d2 / f"{kind}_sum.npy"))
+            assert np.array_equal(sums, [f.astype(np.float64).sum() for f in full])
+            off = 0
+            for f in full:
+                n = min(share, f.size)
+                part = sample[off: off + n]
+                off += n
+                if f.size <= share:
+                    assert np.array_equal(part, f)
+                else:  # drawn from this tensor, and not one value over and over
+                    assert np.isin(part, f).all() and np.unique(part).size > 1
+            assert off == sample.size
+
+
 def test_quantize_model_drop_in(K):
     from types import SimpleNamespace
 

@@ -6,7 +6,7 @@
 #
 #   tests      product GPU suite (pytest -m gpu)          abtests   A/B-library bit-identity suites
 #   subset     pytest -m gpu -k "$PYTEST_K" [$PYTEST_FILES]
-#   smoke      __graft_entry__.smoke()                     bench     python bench.py (the driver's command)
+#   smoke      __graft_entry__.smoke()                     bench     python bench.py --full (every section)
 #   marks      rocprofv3 --kernel-trace --stats of the default bench with --mark-file, cut per bench
 #              region by tools/trace_sections.py (per-workload kernel averages beside bench's numbers)
 #   prof       rocprofv3 --kernel-trace --stats of bench.py (whole run)
@@ -17,7 +17,7 @@
 #   abgemm     tools/ab_gemm.py $AB_GEMM_ARGS             abformats tools/ab_formats_lib.py $AB_FMT_ARGS
 #   ablib      tools/ab_lib.py $AB_LIB_ARGS                gemvcold  tools/bench_gemv_cold.py $GEMV_ARGS
 #   formats    tools/bench_formats.py                      ppl       tools/ppl_delta.py on random OPT-125M
-#   b70        bench.py --model llama2-70b                 inplace   bench.py --inplace
+#   b70        bench.py --full --model llama2-70b          inplace   bench.py --full --inplace
 #   dist2      2 ranks sharing cuda:0 over gloo (the multi-rank plumbing; not a scaling point)
 #   gpmc       MFMA / VALU counters of tools/gemm_pmc.py
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
@@ -45,18 +45,18 @@ for s in "${STEPS[@]}"; do
     abtests) IWQ_AB=1 step pytest_gpu_ab 700 $PYT tests/test_gpu_parity.py tests/test_gpu_approx.py tests/test_gpu_fp_unpack.py -m gpu ;;
     subset) step pytest_subset 900 $PYT ${PYTEST_FILES:-tests} -m gpu -x -k "$PYTEST_K" ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py ;;
+    bench) step bench 600 python bench.py --full ;;
     marks)
       cd /tmp
       step prof_marks 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${T}prof_marks" -o run -- \
-        python3 "$ROOT/bench.py" --mark-file "$OUT/${T}marks.jsonl"
+        python3 "$ROOT/bench.py" --full --mark-file "$OUT/${T}marks.jsonl"
       cd "$ROOT"
       step sections 120 python3 tools/trace_sections.py "$OUT/${T}prof_marks" "$OUT/${T}marks.jsonl" \
         -o "$OUT/${T}sections.json" ;;
     prof)
       cd /tmp
       step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${T}prof" -o run -- \
-        python3 "$ROOT/bench.py" --no-cpu-baseline --steps 10 --warmup 2
+        python3 "$ROOT/bench.py" --full --no-cpu-baseline --steps 10 --warmup 2
       cd "$ROOT" ;;
     pmc)
       cd /tmp
@@ -92,12 +92,12 @@ for s in "${STEPS[@]}"; do
     ppl)
       step ppl_opt125m 600 python tools/ppl_delta.py --random opt-125m --synthetic_tokens 65536 --w_bits 8 4 --w_group_size -2
       step ppl_opt125m_g128 600 python tools/ppl_delta.py --random opt-125m --synthetic_tokens 65536 --w_bits 4 3 --w_group_size 128 ;;
-    b70) step bench70b 900 python bench.py --model llama2-70b --steps 5 --warmup 2 --cpu-seconds 8 ;;
-    inplace) step bench_inplace 600 python bench.py --no-cpu-baseline --inplace ;;
+    b70) step bench70b 900 python bench.py --full --model llama2-70b --steps 5 --warmup 2 --cpu-seconds 8 ;;
+    inplace) step bench_inplace 600 python bench.py --full --no-cpu-baseline --inplace ;;
     dist2)
       export IWQ_DIST_BACKEND=gloo
-      step dist2_7b 600 python bench.py --gpus 2 --steps 5 --warmup 2
-      step dist2_70b 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --model llama2-70b --steps 3 --warmup 1 --no-collectives
+      step dist2_7b 600 python bench.py --full --gpus 2 --steps 5 --warmup 2
+      step dist2_70b 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --model llama2-70b --steps 3 --warmup 1 --no-collectives
       unset IWQ_DIST_BACKEND ;;
     gpmc)
       cd /tmp

@@ -1,4 +1,4 @@
-"""Cut a rocprofv3 kernel trace of `bench.py --mark-file MARKS` into bench.py's timed regions.
+"""Cut a rocprofv3 kernel trace of `bench.py --full --mark-file MARKS` into bench.py's timed regions.
 
 Every number bench.py reports comes from HIP events around one timed region (the headline's K
 launches, each cold `shapes` replay, each fused-forward arm, each formats path, the 70B steps).  With
@@ -9,8 +9,8 @@ duration and (graph replays) the median boundary to the next dispatch, beside be
 figure for that region -- the per-workload rocprof summary each BENCH number is read against.
 
     cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o run -- \\
-        python3 $ROOT/bench.py --mark-file $ROOT/gpurun_out/marks.jsonl
-    python3 tools/trace_sections.py OUT gpurun_out/marks.jsonl -o profiles/rNN_sections.json
+        python3 $ROOT/bench.py --full --mark-file OUT/marks.jsonl
+    python3 tools/trace_sections.py OUT OUT/marks.jsonl -o profiles/rNN_sections.json
 
 Which host clock the trace's timestamps share is found from the data (the clock under which the
 most regions contain a dispatch): rocprofv3 stamps kernels on the system clock of the host.
